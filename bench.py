@@ -10,8 +10,9 @@ resident in HBM, every op in libmigan.so.  Launch-bound steps are captured once 
 segments with the RCCL all-reduce + fused Adam between them on a side stream).
 
 Timing: W warm-up steps, then R >= 1 blocks of EXACTLY K steps, each block bracketed by barrier + synchronize on both
-sides and reduced with MAX over ranks; R is chosen so that the blocks cover >= --min-seconds (default 2 s).  `value` is
-computed from the MEDIAN block (`ms_per_step`); the minimum and every block time are reported next to it.
+sides and reduced with MAX over ranks.  By default R = 1: the run times exactly --steps steps; --min-seconds S repeats the
+block until S seconds are covered.  `value` is computed from the MEDIAN block (`ms_per_step`); the minimum and every block
+time are reported next to it.  --dump-outputs DIR writes what the last timed step computed (see dump_outputs).
 
 Rank 0 prints ONE JSON line.  `roofline` describes the dominant conv kernel of the timed workload, measured live with
 HIP events on the launch stream: `frac` = EXECUTED FLOPs / time / peak (what the matrix pipe did), `frac_dense` = the
@@ -337,6 +338,60 @@ def timed_blocks(w, world, dev, steps, warmup, min_seconds, max_blocks=200):
             more = bool(flag.item() > 0.5)
         if not more:
             return blocks, out
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs: upper bound on what one run writes
+
+
+def step_arrays(w, out):
+    """What a caller of the timed step receives after its last step: the tensors the step returned (losses, generated images)
+    and the floating-point state of the trained networks (parameters, BatchNorm running statistics) - name -> tensor."""
+    arrays = {}
+    for k, v in out.items():
+        if torch.is_tensor(v) and v.is_floating_point():
+            arrays["out." + k] = v
+    for i, net in enumerate(w.nets):
+        for k, t in list(net.named_parameters()) + list(net.named_buffers()):
+            if t.is_floating_point():
+                arrays["net%d.%s" % (i, k)] = t
+    return arrays
+
+
+def dump_outputs(arrays, path, max_bytes=DUMP_BYTES):
+    """Write every array as <path>/<name>.npy (float32, float64 kept), at most `max_bytes` in all: when the whole set does not fit,
+    every array above a common element cap c is replaced by c of its elements at fixed positions (seeded by the array's name), so
+    two builds run with the same arguments write the same elements.  <path>/manifest.json lists full shapes and sample sizes."""
+    import zlib
+
+    if not os.path.isdir(path):   # a directory made here ignores itself in a git tree
+        os.makedirs(path)
+        with open(os.path.join(path, ".gitignore"), "w") as fh:
+            fh.write("*\n")
+    arrays = {k: t.detach() if t.dtype in (torch.float32, torch.float64) else t.detach().float() for k, t in arrays.items()}
+    sizes = {k: (t.numel(), t.element_size()) for k, t in arrays.items()}
+    budget = max_bytes - 256 * (len(arrays) + 64)   # .npy headers and the manifest
+
+    def total(cap):
+        return sum(min(n, cap) * isz for n, isz in sizes.values())
+
+    lo, hi = 0, max((n for n, _ in sizes.values()), default=0)
+    while lo < hi:   # the largest common element cap that fits the budget
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if total(mid) <= budget else (lo, mid - 1)
+    cap = lo
+    manifest = {}
+    for k, t in sorted(arrays.items()):
+        sample = None
+        if t.numel() > cap:
+            sample = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(t.numel(), cap, replace=False))
+            a = t.reshape(-1)[torch.from_numpy(sample).to(t.device)].cpu().numpy()
+        else:
+            a = t.cpu().numpy()
+        np.save(os.path.join(path, k + ".npy"), a)
+        manifest[k] = {"shape": list(t.shape), "dtype": str(a.dtype), "sampled": None if sample is None else int(cap)}
+    with open(os.path.join(path, "manifest.json"), "w") as fh:
+        json.dump({"max_bytes": max_bytes, "sample_seed": "crc32 of the array name", "arrays": manifest}, fh, indent=1)
+    return manifest
 
 
 def summarise(name, batch, world, steps, blocks):
@@ -819,7 +874,8 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the BASELINE config's)")
     ap.add_argument("--global-batch", type=int, default=0,
                     help="strong scaling: total batch, sharded over the ranks (must be divisible by --gpus)")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="repeat the K-step block until this much is timed")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the K-step block until this much is timed (default 0: exactly one block, --steps timed steps)")
     ap.add_argument("--max-blocks", type=int, default=200, help="upper bound on the number of timed K-step blocks")
     ap.add_argument("--no-graph", action="store_true", help="run the step eagerly instead of hipGraph replay")
     ap.add_argument("--graph-always", action="store_true", help="cyclegan: record the step at every batch size (default: batch <= 2 only)")
@@ -828,6 +884,9 @@ def main():
                     "roofline group to this file (tools/pmc_step.py joins it with the pass's counter CSV) and exit")
     ap.add_argument("--no-overlap", action="store_true", help="A/B: one stream - the discriminator update after the generator's backward "
                                                              "(reference order) and every weight gradient in line with its layer's backward")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (its returned tensors and the trained networks' "
+                         "state) as DIR/<name>.npy, at most 64 MB in all (larger sets: a fixed, seeded sample of each large array)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the brief runs of the other BASELINE configs (N=1)")
@@ -906,6 +965,9 @@ def main():
         print(json.dumps({"pmc_log": args.pmc_log, "segments": len(segs), "total_launches": lib.migan_debug_launch_count(None)}))
         return
     blocks, out = timed_blocks(w, world, dev, args.steps, args.warmup, args.min_seconds, max_blocks=args.max_blocks)
+    if args.dump_outputs and rank == 0:   # before anything below runs another step on the same state
+        torch.cuda.synchronize()
+        dump_outputs(step_arrays(w, out), args.dump_outputs)
     exchange = None
     if world > 1 and hasattr(dp, "start_timing"):
         # what the exchange costs and how much of it the overlap hides: HIP events around every bucket all-reduce (side stream) and

@@ -124,6 +124,38 @@ def test_bench_flop_accounting_and_pmc_table():
             assert 0.0 <= ent["mfma_busy_frac"] <= 1.0
 
 
+def test_bench_dump_outputs_stays_in_budget_and_samples_the_same_elements(tmp_path):
+    """bench.py --dump-outputs: the step's returned tensors and the networks' floating-point state, one .npy each; a set over the
+    byte budget is cut to a common element cap with positions seeded by the array's name, so two runs write the same elements."""
+    import types
+
+    import numpy as np
+
+    import bench
+
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(1000, 3000), torch.nn.BatchNorm1d(3000))
+    w = types.SimpleNamespace(nets=(net,))
+    out = {"g_loss": torch.tensor(0.25), "gen_imgs": torch.randn(64, 1, 64, 64), "step": 3}
+    arrays = bench.step_arrays(w, out)
+    assert set(arrays) == {"out.g_loss", "out.gen_imgs", "net0.0.weight", "net0.0.bias", "net0.1.weight", "net0.1.bias",
+                           "net0.1.running_mean", "net0.1.running_var"}
+    budget = 4 << 20
+    a, b, full = tmp_path / "a", tmp_path / "b", tmp_path / "full"
+    man = bench.dump_outputs(arrays, str(a), max_bytes=budget)
+    bench.dump_outputs(arrays, str(b), max_bytes=budget)
+    assert sum(f.stat().st_size for f in a.iterdir()) <= budget and (a / ".gitignore").read_text() == "*\n"
+    assert man["net0.0.weight"]["sampled"] and man["net0.0.weight"]["shape"] == [3000, 1000] and man["out.gen_imgs"]["sampled"] is None
+    for k in arrays:
+        x, y = np.load(a / (k + ".npy")), np.load(b / (k + ".npy"))
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+    sampled = np.load(a / "net0.0.weight.npy")
+    assert np.isin(sampled, net[0].weight.detach().numpy().reshape(-1)).all()
+    bench.dump_outputs(arrays, str(full))   # fits the default budget: every element
+    assert np.array_equal(np.load(full / "net0.0.weight.npy"), net[0].weight.detach().numpy())
+    assert np.load(full / "out.g_loss.npy") == np.float32(0.25)
+
+
 def test_sequential_fusion_plan(monkeypatch):
     """Which launcher families nn.Sequential routes the reference's layer patterns to (no kernels run: the functional
     entry points are replaced by recorders that only produce tensors of the right shape)."""
